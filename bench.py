@@ -12,11 +12,23 @@ the timed region -- packets are independent (compress.c:252-265), so this is
 weak scaling.  The RCCL scatter/gather of a batch from rank 0 is timed
 separately and reported in "rccl_scatter_gather".
 
-Extra fields: "roofline" (dominant kernel, algorithmic HBM bytes / measured
-kernel time vs 8 TB/s), "cpu_baseline" (reference compress.c on host cores,
-rank 0 only), "pcie_inclusive" (H2D + kernels + D2H from pinned memory),
-"datagram_path" (whole ENet datagrams: GPU framing + checksum + coder, and the
-UDP -> pinned staging -> GPU decode pipeline).
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure
+needs and no more: set up, W warm-up steps, K timed steps, the result line.
+"roofline" (dominant kernel, algorithmic HBM bytes / its HIP-event time inside
+the timed steps vs 8 TB/s) rides on those same steps.
+
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs)
+as DIR/<name>.npy; the inputs are a function of the arguments alone, so two
+builds can be compared output for output.
+
+`--full` adds the side measurements, each in runs of its own after the timed
+steps: "configs" (the other BASELINE configs C3, C4), "crc32", "cpu_baseline"
+(reference compress.c on host cores, rank 0 only), "pcie_inclusive" (H2D +
+kernels + D2H from pinned memory), "datagram_path" (whole ENet datagrams: GPU
+framing + checksum + coder, and the UDP -> pinned staging -> GPU decode
+pipeline), "per_datagram_call", "multi_device_c_abi"
+and, on more than one GPU, "rccl_scatter_gather".  The `--no-*` options drop
+single legs of a `--full` run.
 """
 import argparse
 import json
@@ -41,6 +53,11 @@ def parse():
     p.add_argument("--workload", default="c2", choices=["c2", "c3", "c4"])
     p.add_argument("--packets", type=int, default=65536)
     p.add_argument("--size", type=int, default=1200)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy (rank 0's shard)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the side measurements (other configs, CRC-32, PCIe-inclusive, datagram path, "
+                        "multi-device C entry, RCCL scatter/gather, CPU baseline); the --no-* options drop single ones")
     p.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="cpu_baseline threads (0: every CPU in this process's affinity mask)")
@@ -50,7 +67,12 @@ def parse():
     p.add_argument("--no-dgram", action="store_true", help="skip the datagram-path leg")
     p.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configs (C3, C4)")
     p.add_argument("--no-multi", action="store_true", help="skip the multi-GPU C-ABI leg")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:
+        # a plain run: the headline's steps alone, every side measurement off
+        for leg in ("cpu", "pcie", "crc", "rccl", "dgram", "configs", "multi"):
+            setattr(args, "no_" + leg, True)
+    return args
 
 
 def make_batch(kind, n, size, rank):
@@ -178,8 +200,88 @@ def run_workload(coder, dev, stream, kind, n, size, rank, steps, warmup, dist=No
         "roofline": roofline,
     }
     raw = dict(d=d, o=o, l=l, din=din, doff=doff, dlen=dlen, in_bytes=in_bytes, n=n, max_len=max_len,
-               elapsed=elapsed, t_dom=t_dom, kname=kname)
+               elapsed=elapsed, t_dom=t_dom, kname=kname,
+               outputs=dict(cout=cout, coff=coff, clen=clen, dout=dout, doff=doff, dl=dl, dlen=dlen))
     return raw, summary
+
+
+DUMP_SEED = 0x44554D50             # "DUMP": the sampled packets are a function of this and the batch alone
+DUMP_MAX_PACKETS = 1 << 20         # the per-packet arrays cover every packet up to this many (C4), else a sample
+DUMP_SAMPLE_BYTES = 2 << 20        # uncompressed bytes of the packets written out byte for byte
+DUMP_LIMIT = 64 * 1000 * 1000      # bytes in all
+
+
+def packed_packets(buf, off, ln):
+    """Packets buf[off[i] : off[i] + ln[i]] back to back (none of the unwritten
+    room between output slots), and each packet's start in that array."""
+    import torch
+    ln = ln.to(torch.int64)
+    start = torch.cumsum(ln, 0) - ln
+    total = int(ln.sum().item())
+    idx = torch.repeat_interleave(off.to(torch.int64) - start, ln) + torch.arange(total, device=buf.device)
+    return buf[idx], start
+
+
+def packet_sums(buf, off, ln):
+    """Per packet, sum over its bytes of (position in the packet + 1) x byte:
+    every byte of every packet and its place count (exact in float64)."""
+    import torch
+    b, start = packed_packets(buf, off, ln)
+    ln = ln.to(torch.int64)
+    pos = torch.arange(b.numel(), device=b.device) - torch.repeat_interleave(start, ln)
+    c = torch.zeros(b.numel() + 1, dtype=torch.int64, device=b.device)
+    torch.cumsum(b.to(torch.int64) * (pos + 1), 0, out=c[1:])
+    return (c[start + ln] - c[start]).cpu().numpy().astype(np.float64)
+
+
+def dump_outputs(path, outputs):
+    """What a caller of the timed path holds after its last step, as
+    <path>/<name>.npy (float32 / float64, under 64 MB in all):
+
+      packets            the packets the per-packet arrays speak of (all of
+                         them up to 1 Mi packets, else a fixed seeded sample)
+      compressed_len     compress_batch's lengths           } of those packets
+      decompressed_len   decompress_batch's lengths         }
+      compressed_sum     packet_sums of the compressed bytes   (every byte of
+      decompressed_sum   packet_sums of the decompressed bytes  the outputs counts)
+      sample_packets     a fixed seeded sample of packets (~2 MiB of payload) ...
+      compressed_sample  ... their compressed bytes back to back, byte for byte
+      decompressed_sample ... and their decompressed bytes
+    """
+    import torch
+    from enet_amd import synth
+    cout, coff, clen = outputs["cout"], outputs["coff"], outputs["clen"]
+    dout, doff, dl = outputs["dout"], outputs["doff"], outputs["dl"]
+    if cout.is_cuda:
+        torch.cuda.synchronize()
+    n = clen.numel()
+    clen_h = clen.cpu().numpy().astype(np.int64)
+    dl_h = dl.cpu().numpy().astype(np.int64)
+    # the lengths are written as they came; the bytes are read inside each packet's slot whatever they say
+    room = outputs["dlen"].to(torch.int64)
+    clen = torch.minimum(clen.to(torch.int64).clamp(min=0), 2 * room + 64)
+    dl = torch.minimum(dl.to(torch.int64).clamp(min=0), room)
+    order = np.argsort(synth.splitmix64(DUMP_SEED, n), kind="stable")       # a fixed shuffle of the packets
+    pk = np.sort(order[:DUMP_MAX_PACKETS])
+    # the sample: the shuffle's longest prefix within the byte budget (by the packets' input sizes alone)
+    fits = np.cumsum(room.cpu().numpy()[order]) <= DUMP_SAMPLE_BYTES
+    sp = np.sort(order[:max(1, int(fits.sum()))])
+    spd = torch.from_numpy(sp).to(clen.device)
+    arrays = {
+        "packets": pk.astype(np.float64),
+        "compressed_len": clen_h[pk].astype(np.float32),
+        "decompressed_len": dl_h[pk].astype(np.float32),
+        "compressed_sum": packet_sums(cout, coff, clen)[pk],
+        "decompressed_sum": packet_sums(dout, doff, dl)[pk],
+        "sample_packets": sp.astype(np.float64),
+        "compressed_sample": packed_packets(cout, coff[spd], clen[spd])[0].cpu().numpy().astype(np.float32),
+        "decompressed_sample": packed_packets(dout, doff[spd], dl[spd])[0].cpu().numpy().astype(np.float32),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs would write {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def free_port():
@@ -281,6 +383,10 @@ def main():
     roofline = main_line["roofline"]
     roofline["compress_ms"] = main_line["compress_ms"]
     roofline["decompress_ms"] = main_line["decompress_ms"]
+    outputs = raw.pop("outputs")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    del outputs
 
     result = {
         "metric": "GiB/s device-resident range-coder (de)compress, 64Ki×1200B pkts, 1/2/4/8 GPU",
@@ -317,7 +423,7 @@ def main():
         # the other single-GPU BASELINE configs, measured in the same run
         # (C2 is the headline above); fewer steps: each is a full batch
         def other(kind, packets):
-            del_keys = ("d", "o", "l", "din", "doff", "dlen")
+            del_keys = ("d", "o", "l", "din", "doff", "dlen", "outputs")
             r, summ = run_workload(coder, dev, stream, kind, packets, 1200, rank, 3, 1)
             for k in del_keys:
                 r.pop(k, None)

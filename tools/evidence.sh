@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round evidence on one GPU box.  usage: tools/evidence.sh TAG [bench] [c2] [c3] [c4]
-#   bench: the default bench line (C2 headline with the C3/C4 configs,
+#   bench: the full bench line (bench.py --full: C2 headline with the C3/C4 configs,
 #          cpu_baseline, PCIe-inclusive rate, CRC-32, datagram path, multi-GPU
 #          C-ABI leg) and the host-path phase profile;
 #   c2|c3|c4: rocprofv3 kernel trace + PMC passes of that workload's bench
@@ -17,7 +17,7 @@ WHAT="$*"; [ -z "$WHAT" ] && WHAT="bench c2 c3 c4"
 for what in $WHAT; do
   case $what in
     bench)
-      timeout -k 10 500 python bench.py > $O/bench.log 2>&1
+      timeout -k 10 500 python bench.py --full > $O/bench.log 2>&1
       timeout -k 10 120 python tools/pcie_prof.py > $O/pcie_phases.log 2>&1 ;;
     c2|c3|c4)
       P=65536; [ $what = c4 ] && P=1048576
