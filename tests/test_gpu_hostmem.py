@@ -1,16 +1,18 @@
-"""Host-pointer batches and the caller's memory (rc_host.c run_host /
-host_results), against the oracle:
+"""Host-pointer batches and the caller's memory (rc_hostmem.c), against the
+oracle:
 
 - the GPU gather of a gapped compressed input over the caller's mapped,
   page-locked range (rc_gather16 over a buffer the caller page-locked) when
   the CPU rewrites that buffer between calls, and when the buffer is freed
   and a new one takes its place -- the round-5 review's candidate (b) for the
   r5a wrong decode (stale lines of mapped pages); the same batches from
-  pageable memory take the pinned staging (pageable caller memory is not
-  page-locked per call unless ENET_RC_HOST_REGISTER=1);
+  pageable memory take the pinned staging (the library never page-locks
+  caller memory);
 - back-to-back output slots that some packets do not fill (corrupt streams):
   the caller's bytes past each out_len stay as they were, as compress.c
-  writes only what it decodes (round-5 ADVICE: the one-DMA result path).
+  writes only what it decodes (round-5 ADVICE: the one-DMA result path);
+- every input and result route, and a split batch, over memory the caller
+  page-locked (enet_rc_last_host_paths).
 """
 import ctypes as C
 
@@ -131,6 +133,101 @@ def test_back_to_back_slots_keep_bytes_past_out_len(rc, mem):
             s = int(o[i])
             assert np.array_equal(dout[s: s + int(got[i])], want[int(wo[i]): int(wo[i]) + int(wl[i])]), i
             assert (dout[s + int(got[i]): s + size] == 0x3C).all(), i
+
+
+@pytest.fixture(scope="module")
+def route_batch():
+    """32768 random 1200-B packets and their oracle streams (read-only): the
+    route cases take the first 14336 (17.2 MB, just over the 16 MiB threshold
+    of the gather and slot-copy routes), the split case all of them."""
+    from oracle.pyoracle import compress_batch
+    d, o, l = synth.random_batch(32768, 1200, seed=0x5A35)
+    out, oo, cap, ol = compress_batch(d, o, l, "port")
+    for a in (d, o, l, out, oo, cap, ol):
+        a.setflags(write=False)
+    return d, o, l, out, oo, cap, ol
+
+
+def _gapped(cap, n):
+    """Slots of cap[i] bytes with non-uniform gaps (0..6 bytes) between them."""
+    off = np.zeros(n, np.uint64)
+    off[1:] = np.cumsum(cap[:n - 1].astype(np.uint64) + (np.arange(n - 1, dtype=np.uint64) % np.uint64(7)))
+    return off, int(off[-1]) + int(cap[n - 1]) + 16
+
+
+def _slot_mismatches(buf, boff, want, woff, wlen):
+    return [i for i in range(len(wlen))
+            if not np.array_equal(buf[int(boff[i]): int(boff[i]) + int(wlen[i])],
+                                  want[int(woff[i]): int(woff[i]) + int(wlen[i])])][:8]
+
+
+@pytest.mark.parametrize("case,mem,n,layout,paths", [
+    ("compress", "pinned", 14336, "packed", (2, 3)),       # one DMA of the caller's range in, GPU slot copy out
+    ("compress", "pinned", 14336, "pitch", (3, 3)),        # strided DMA of slots at pitch 1216 in
+    ("decompress", "pinned", 14336, "gapped", (4, 2)),     # GPU gather in, one DMA of the span out
+    ("compress", "pageable", 14336, "packed", (1, 4)),     # staging in, device pack + host scatter out
+    ("compress", "pinned", 64, "packed", (1, 1)),          # below the 1 MiB floor: staging in, small copy out
+])
+def test_host_routes(rc, route_batch, case, mem, n, layout, paths):
+    """The input and result routes of a host batch (rc_hostmem.c), each asserted
+    by both nibbles of enet_rc_last_host_paths and bit-exact against the oracle."""
+    d, o, l, want, wo, wcap, wl = route_batch
+    buf = _pinned if mem == "pinned" else (lambda nbytes, fill: np.full(nbytes, fill, np.uint8))
+    ln, cl = np.ascontiguousarray(l[:n]), np.ascontiguousarray(wl[:n])
+    got = np.zeros(n, np.uint32)
+    if case == "compress":
+        pitch = 1200 if layout == "packed" else 1216
+        ioff = np.arange(n, dtype=np.uint64) * np.uint64(pitch)
+        din = buf(n * pitch, 0x77)
+        din.reshape(n, pitch)[:, :1200] = d[: n * 1200].reshape(n, 1200)
+        cap = np.ascontiguousarray(wcap[:n])
+        coff, total = _gapped(cap, n)
+        cout = buf(total, 0xC3)
+        assert rc.lib.enet_rc_compress_batch_host(rc.ctx, P(din), P(ioff), P(ln), n, P(cout), P(coff), P(cap),
+                                                  P(got)) == 0
+        p = rc.lib.enet_rc_last_host_paths(rc.ctx)
+        assert (p & 0xF, p >> 4) == paths, hex(p)
+        assert np.array_equal(got, cl)
+        assert not _slot_mismatches(cout, coff, want, wo, cl)
+    else:
+        assert int(cl.sum(dtype=np.uint64)) >= 16 << 20     # else the gather route is not the one under test
+        coff, total = _gapped(cl, n)
+        cin = buf(total, 0xC3)
+        for i in range(n):
+            cin[int(coff[i]): int(coff[i]) + int(cl[i])] = want[int(wo[i]): int(wo[i]) + int(cl[i])]
+        dout = buf(n * 1200 + 16, 0x3C)
+        doff = np.ascontiguousarray(o[:n])
+        assert rc.lib.enet_rc_decompress_batch_host(rc.ctx, P(cin), P(coff), P(cl), n, P(dout), P(doff), P(ln),
+                                                    P(got)) == 0
+        p = rc.lib.enet_rc_last_host_paths(rc.ctx)
+        assert (p & 0xF, p >> 4) == paths, hex(p)
+        assert np.array_equal(got, ln)
+        assert np.array_equal(dout[: n * 1200], d[: n * 1200])
+
+
+def test_host_split_over_pinned_memory(rc, route_batch):
+    """A split batch (default ENET_RC_HOST_SPLIT) whose buffers the caller
+    page-locked: 32768 x 1200 B compressed into gapped slots, then decompressed
+    into back-to-back slots; bit-exact against the oracle both ways."""
+    import os
+    d, o, l, want, wo, wcap, wl = route_batch
+    n = len(l)
+    pieces = min(3, max(int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) - 1, 1))
+    din = _pinned(d.size)
+    din[:] = d
+    coff, total = _gapped(wcap, n)
+    cout = _pinned(total, 0xC3)
+    clen = np.zeros(n, np.uint32)
+    assert rc.lib.enet_rc_compress_batch_host(rc.ctx, P(din), P(o), P(l), n, P(cout), P(coff), P(wcap), P(clen)) == 0
+    assert rc.lib.enet_rc_last_split(rc.ctx) == pieces
+    assert np.array_equal(clen, wl)
+    assert not _slot_mismatches(cout, coff, want, wo, wl)
+    dout = _pinned(d.size + 16, 0x3C)
+    dlen = np.zeros(n, np.uint32)
+    assert rc.lib.enet_rc_decompress_batch_host(rc.ctx, P(cout), P(coff), P(clen), n, P(dout), P(o), P(l), P(dlen)) == 0
+    assert rc.lib.enet_rc_last_split(rc.ctx) == pieces
+    assert np.array_equal(dlen, l)
+    assert np.array_equal(dout[: d.size], d)
 
 
 def test_slot_handoff_many_packets_per_lane(rc):

@@ -454,7 +454,7 @@ def test_small_batches_vs_oracle(coder):
 
 def test_host_pointer_batches_large(coder):
     """enet_rc_{compress,decompress}_batch_host on a batch large enough for the
-    chunked staging copies, device-side packing and chunked D2H (rc_host.c
+    chunked staging copies, device-side packing and chunked D2H (rc_hostmem.c
     run_host, rc_pack.hip): bit-exact against the oracle, ragged offsets."""
     import ctypes as C
     from oracle.pyoracle import compress_batch as ocompress, fnv_digest
@@ -486,8 +486,9 @@ def test_host_pointer_batches_large(coder):
 @pytest.mark.parametrize("pieces", [3, 4])
 def test_host_pointer_batches_pieces(pieces):
     """ENET_RC_HOST_SPLIT=k: a large host batch in k pieces on k contexts of
-    the device (rc_host.c run_host_split: each piece's input DMA after the
-    previous piece's), at equal shares of the input bytes; ragged packets,
+    the device (rc_hostmem.c run_host_split: each piece's input DMA after the
+    previous piece's), at equal shares of the input bytes, each piece through
+    its own pinned staging (the buffers are pageable); ragged packets,
     bit-exact against the oracle both ways."""
     import os
     import ctypes as C
@@ -536,11 +537,12 @@ def test_host_pointer_batches_pieces(pieces):
 
 
 def test_host_pointer_batches_pieces_ragged():
-    """Split host batches (three pieces, rc_host.c run_host_split) on a ragged
+    """Split host batches (three pieces, rc_hostmem.c run_host_split) on a ragged
     batch: 52100 packets of 0-2000 B (every 50th empty, a packet count that
     is no multiple of the 2048-packet piece groups), inputs in gapped slots
-    both ways and decompress outputs in gapped slots too (the slot-copy
-    result path instead of the one-DMA one); bit-exact against the oracle."""
+    both ways and decompress outputs in gapped slots too (pageable buffers:
+    staged in on the copy threads, packed on the device and scattered on the
+    host); bit-exact against the oracle."""
     import os
     import ctypes as C
     from enet_amd import RangeCoder
@@ -602,7 +604,7 @@ def test_host_pointer_batches_pieces_ragged():
 
 def test_host_pointer_batches_split(coder):
     """A host batch of >= 32768 packets and >= 32 MB runs in two halves on two
-    contexts of the device (rc_host.c run_host_split: the second half's input
+    contexts of the device (rc_hostmem.c run_host_split: the second half's input
     DMA after the first's, the halves' kernels side by side): bit-exact
     against the oracle both ways, gapped compressed slots, and the hand-off
     counts of both halves reported together."""
@@ -662,9 +664,10 @@ def test_host_pointer_batches_split(coder):
 
 def test_host_pointer_batches_uniform_slots(coder):
     """Host batches whose compressed packets sit in slots at a uniform, odd
-    pitch from an odd base (rc_host.c run_host: the strided H2D of max_len
-    bytes per slot for the decompress input; the GPU scatter of the packed
-    results into the caller's slots for the compress output): bit-exact
+    pitch from an odd base, in pageable buffers (rc_hostmem.c run_host: the
+    decompress input staged on the copy threads, the compress output packed
+    on the device and scattered on the host; the strided DMA and the GPU slot
+    copy over page-locked buffers are test_gpu_hostmem.py's): bit-exact
     against the oracle, the last slot's bytes beyond its packet untouched."""
     import ctypes as C
     from oracle.pyoracle import compress_batch as ocompress, fnv_digest
@@ -710,7 +713,7 @@ def test_device_decoder_bounded_vs_oracle(coder):
 
 
 def test_host_pointer_decoder_sized_by_out_cap(coder):
-    """Host-pointer decompress batches pass max(out_cap) down (rc_host.c
+    """Host-pointer decompress batches pass max(out_cap) down (rc_hostmem.c
     run_host), so the wave decoder sizes its LDS arena by the output bound
     and batches of 513-1024 packets of <= 1400 B now fit on the chip at one
     wavefront per packet (rc_kernels.hip wave_lds).  Bit-exact against the

@@ -1,5 +1,5 @@
 """PCIe / host-copy / registration rates on the GPU box (diagnostic for the
-host-pointer path, rc_host.c run_host)."""
+host-pointer path, rc_hostmem.c run_host)."""
 import ctypes as C, time
 import numpy as np, torch
 hip = C.CDLL("libamdhip64.so")

@@ -1,4 +1,4 @@
-"""Host batches in k pieces (k = 0: as ENET_RC_HOST_SPLIT says) (rc_host.c run_host_split, ENET_RC_HOST_SPLIT=k):
+"""Host batches in k pieces (k = 0: as ENET_RC_HOST_SPLIT says) (rc_hostmem.c run_host_split, ENET_RC_HOST_SPLIT=k):
 the PCIe-inclusive round trip of bench.py's pcie leg for each k, interleaved
 in one process, best of R per k.  usage: python tools/split_ab.py [ks] [rounds] [workload]"""
 import os
