@@ -31,6 +31,9 @@ extern "C" __global__ void udiv_check(uint64_t seed, uint32_t iters, unsigned lo
         const uint32_t q16 = a0 / b16;
         const uint32_t c16[4] = {a0, q16 * b16, q16 * b16 ? q16 * b16 - 1 : 0u, 0xFFFFFFFFu};
         for (int c = 0; c < 4; ++c) nbad += udiv16(c16[c], b16) != c16[c] / b16;
+        // udiv16r: the same quotient with the reciprocal at hand (rcp16)
+        const float f16 = rcp16(b16);
+        for (int c = 0; c < 4; ++c) nbad += udiv16r(c16[c], b16, f16) != c16[c] / b16;
         // udiv16d: the same divisors, the double-precision quotient
         const double r16 = rcp64(b16);
         for (int c = 0; c < 4; ++c) nbad += udiv16d(c16[c], b16, r16) != c16[c] / b16;
