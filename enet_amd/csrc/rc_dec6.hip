@@ -83,7 +83,16 @@ namespace {
 #ifndef DEC6_RARE_ITERS
 #define DEC6_RARE_ITERS 2
 #endif
+#ifndef DEC6_TAIL
+#define DEC6_TAIL 0                // 0-3: steps between the record loads and the rare phase (0: loaded in the phase)
+#endif
+#if DEC6_TAIL < 0 || DEC6_TAIL > 3
+#error "DEC6_TAIL: 0-3"
+#endif
+#define DEC6_STEP_INLINE __attribute__((always_inline))
 constexpr uint32_t kBlock6 = DEC6_BLOCK;        // common steps between rare phases
+constexpr uint32_t kTail6 = DEC6_TAIL;          // ... the last of them behind the record loads
+static_assert(kTail6 < kBlock6, "DEC6_TAIL: below DEC6_BLOCK");
 constexpr uint32_t kRareIters6 = DEC6_RARE_ITERS;   // rare steps per phase and lane
 constexpr uint32_t kWaveBail6 = 16;
 constexpr uint32_t kStats6 = kRootStrideDec;     // the LDS bucket bytes follow the root
@@ -193,7 +202,7 @@ DEV void sink1_finish(ByteSink1& o)
 template <class Src>
 DEV void decompress_one6(const rc_batch_dev& bt, const rc_workspace_dev& ws, uint32_t pkt, uint8_t* root,
                          uint8_t* stats, uint8_t* tab, uint8_t* tab2, const uint8_t* itab, Src& in,
-                         const double* rtab = nullptr)
+                         const double* rtab = nullptr, const uint8_t* dum = nullptr)
 {
     constexpr bool kSlot = std::is_same<Src, SlotSrc>::value;
     const uint32_t len = bt.in_len[pkt];
@@ -237,147 +246,191 @@ DEV void decompress_one6(const rc_batch_dev& bt, const rc_workspace_dev& ws, uin
     // a lane that stores no element stores to its dummy slot -- so that the
     // compiler can wait for an input chunk with vmcnt(n) rather than behind
     // every store in flight (see rc_lane3.hip lane_prefetch).
-    uint32_t s = 0;
 #ifdef DEC6_STATS_PREFETCH
     uint32_t stn = 0;
     double rtn = 1.0;                         // 1 / the order-1 total of the next step's bucket
 #endif
-    for (;;) {
-        {
-            // ------------------------------------------------------ a common step
-            uint32_t shc = 0;                                  // (SlotSrc: h_ctl and the slot, used at the end)
-            uint4 ssl = make_uint4(0u, 0u, 0u, 0u);
-            if constexpr (kSlot) {
-                slot_read(in, shc, ssl);
-            } else {
-                src_fill(in, true);
-            }
-            sink1_flush(o);
-            const bool go = !done && !stall;
+    auto step = [&]() DEC6_STEP_INLINE {
+        // ------------------------------------------------------ a common step
+        uint32_t shc = 0;                                  // (SlotSrc: h_ctl and the slot, used at the end)
+        uint4 ssl = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (kSlot) {
+            slot_read(in, shc, ssl);
+        } else {
+            src_fill(in, true);
+        }
+        sink1_flush(o);
+        const bool go = !done && !stall;
 #ifdef DEC6_STATS_PREFETCH
-            const uint32_t st = (go && order >= 1) ? stn : 0u;
+        const uint32_t st = (go && order >= 1) ? stn : 0u;
 #else
-            const uint32_t sraw = stats[p];                    // (read on every path: no exec mask)
-            const uint32_t st = (go && order >= 1) ? sraw : 0u;
+        const uint32_t sraw = stats[p];                    // (read on every path: no exec mask)
+        const uint32_t st = (go && order >= 1) ? sraw : 0u;
 #endif
-            const uint32_t t1 = st & 31u, d1 = t1 - (st >> 5);
-            bool need = go && order >= 2 && repeat && !o2s;
-            // order 2 when its context holds one visit: an escape is coded here, the
-            // context's one symbol stalls the lane (compress.c:536-568 over total 7)
-            bool e2 = false;
-            const bool c2s = go && order >= 2 && repeat && o2s;
-            if (any_lane(c2s)) {
-                const uint32_t r2 = udiv16d(range, 7u, 1.0 / 7.0);
-                e2 = c2s && code - low < 5u * r2;
-                need = need || (c2s && !e2);
-                range = e2 ? r2 : range;
-                dec_code(low, code, range, 0u, 5u, in, e2);
-            }
-            // order 1 (compress.c:536-568): READ; an escape is coded here, a hit stalls the lane
-            const bool o1 = go && !need && order >= 1 && t1 > 0;
-            const uint32_t esc1 = kSubEscDelta * d1, tot1 = o1 ? esc1 + kSubDelta * t1 : 1u;
+        const uint32_t t1 = st & 31u, d1 = t1 - (st >> 5);
+        bool need = go && order >= 2 && repeat && !o2s;
+        // order 2 when its context holds one visit: an escape is coded here, the
+        // context's one symbol stalls the lane (compress.c:536-568 over total 7)
+        bool e2 = false;
+        const bool c2s = go && order >= 2 && repeat && o2s;
+        if (any_lane(c2s)) {
+            const uint32_t r2 = udiv16d(range, 7u, 1.0 / 7.0);
+            e2 = c2s && code - low < 5u * r2;
+            need = need || (c2s && !e2);
+            range = e2 ? r2 : range;
+            dec_code(low, code, range, 0u, 5u, in, e2);
+        }
+        // order 1 (compress.c:536-568): READ; an escape is coded here, a hit stalls the lane
+        const bool o1 = go && !need && order >= 1 && t1 > 0;
+        const uint32_t esc1 = kSubEscDelta * d1, tot1 = o1 ? esc1 + kSubDelta * t1 : 1u;
 #ifdef DEC6_STATS_PREFETCH
-            const uint32_t r1 = udiv16d(range, tot1, o1 ? rtn : 1.0);
+        const uint32_t r1 = udiv16d(range, tot1, o1 ? rtn : 1.0);
 #elif defined(DEC6_RCP_TAB) && !defined(RC_LANE_HOST_TEST)
-            // (1 / the order-1 total from the block's table by the bucket byte: a
-            // lane without an order-1 code reads an entry it does not use; -0.3 %,
-            // within noise: profiles/r6/r6e_dec6_prefetch_rcptab_ab_c2.txt)
-            const uint32_t r1 = udiv16d(range, tot1, rtab[st]);
+        // (1 / the order-1 total from the block's table by the bucket byte: a
+        // lane without an order-1 code reads an entry it does not use; -0.3 %,
+        // within noise: profiles/r6/r6e_dec6_prefetch_rcptab_ab_c2.txt)
+        const uint32_t r1 = udiv16d(range, tot1, rtab[st]);
 #else
-            const uint32_t r1 = udiv16d(range, tot1, rcp64(tot1));
+        const uint32_t r1 = udiv16d(range, tot1, rcp64(tot1));
 #endif
 #ifndef DEC6_READ1
-            // READ < escapes without the READ's division: (code - low) / r1 < esc1
-            // iff code - low < esc1 r1 (the quotient is then below 2^16: no
-            // truncation, compress.c:352); otherwise a hit -- or, on a corrupt
-            // stream, a quotient truncated to 16 bits -- both for the rare step,
-            // which READs in full
-            const bool e1 = o1 && code - low < esc1 * r1;
-            need = need || (o1 && !e1);
+        // READ < escapes without the READ's division: (code - low) / r1 < esc1
+        // iff code - low < esc1 r1 (the quotient is then below 2^16: no
+        // truncation, compress.c:352); otherwise a hit -- or, on a corrupt
+        // stream, a quotient truncated to 16 bits -- both for the rare step,
+        // which READs in full
+        const bool e1 = o1 && code - low < esc1 * r1;
+        need = need || (o1 && !e1);
 #else
-            const uint32_t cd1 = udiv_lo16(code - low, r1);
-            need = need || (o1 && cd1 >= esc1);
-            const bool e1 = o1 && cd1 < esc1;
+        const uint32_t cd1 = udiv_lo16(code - low, r1);
+        need = need || (o1 && cd1 >= esc1);
+        const bool e1 = o1 && cd1 < esc1;
 #endif
-            need = need && !(ws.dec6_debug & 2);      // (timing experiment: no rare steps, output lost)
-            range = e1 ? r1 : range;
-            dec_code(low, code, range, 0u, esc1, in, e1);
-            // the root (compress.c:570-596)
-            const bool rg = go && !need;
-            const uint32_t r0 = udiv16d(range, rtot, rrt);
-            const uint32_t cd0 = udiv_lo16(code - low, r0);
-            const bool eos = rg && cd0 < 1;                                // end of stream
-            const bool past = rg && !eos && cd0 - 1 >= rtot - 1;           // past symbol 255: exact path
-            const bool sym = rg && !eos && !past;
-            range = sym ? r0 : range;
-            uint32_t under0 = 0, cnt0 = 0;
+        need = need && !(ws.dec6_debug & 2);      // (timing experiment: no rare steps, output lost)
+        range = e1 ? r1 : range;
+        dec_code(low, code, range, 0u, esc1, in, e1);
+        // the root (compress.c:570-596)
+        const bool rg = go && !need;
+        const uint32_t r0 = udiv16d(range, rtot, rrt);
+        const uint32_t cd0 = udiv_lo16(code - low, r0);
+        const bool eos = rg && cd0 < 1;                                // end of stream
+        const bool past = rg && !eos && cd0 - 1 >= rtot - 1;           // past symbol 255: exact path
+        const bool sym = rg && !eos && !past;
+        range = sym ? r0 : range;
+        uint32_t under0 = 0, cnt0 = 0;
 #ifndef DEC6_ITAB_LATE
-            uint4 i0, i1;
-            const uint32_t v = root3_search_inc(root, R, itab, sym ? cd0 - 1 : 0u, under0, cnt0, i0, i1);
+        uint4 i0, i1;
+        const uint32_t v = root3_search_inc(root, R, itab, sym ? cd0 - 1 : 0u, under0, cnt0, i0, i1);
 #else
-            const uint32_t v = root3_search(root, R, sym ? cd0 - 1 : 0u, under0, cnt0);
+        const uint32_t v = root3_search(root, R, sym ? cd0 - 1 : 0u, under0, cnt0);
 #endif
-            dec_code_late(low, code, range, 1 + under0, 1 + cnt0, in, sym);
-            if (sym) {
+        dec_code_late(low, code, range, 1 + under0, 1 + cnt0, in, sym);
+        if (sym) {
 #ifndef DEC6_ITAB_LATE
-                root3_add_pre(root, R, v, cnt0, i0, i1);
+            root3_add_pre(root, R, v, cnt0, i0, i1);
 #else
-                root3_add_inc(root, R, itab, v, cnt0);
+            root3_add_inc(root, R, itab, v, cnt0);
 #endif
-                rtot = (rtot + kRootDelta) & 0xFFFF;
-            }
-            if (rare_lane(sym && (1 + cnt0 > 0xFF - 2 * kRootDelta + 1 || rtot > kTotalLimit))) {
-                if (sym && (1 + cnt0 > 0xFF - 2 * kRootDelta + 1 || rtot > kTotalLimit))
-                    rtot = root3_rescale<false>(root, R);
-            }
-            rrt = sym ? rcp64(rtot) : rrt;
-            // the element joins bucket p: new to its order-2 context (never visited) and,
-            // by the assumption above, to order 1; nodes as compress.c creates them
-            nodes += sym ? (cnt0 == 0 ? 1u : 0u) + (order >= 1 ? 1u : 0u) + (order >= 2 ? 1u : 0u) : 0u;
-            const bool o1v = sym && order >= 1;
-#ifndef DEC6_STATS_PREFETCH
-            stats[p] = static_cast<uint8_t>(o1v ? st + 1 : sraw);   // (written on every path: no exec mask)
-#else
-            if (o1v) stats[p] = static_cast<uint8_t>(st + 1);
-#endif
-            const bool full = o1v && t1 >= kTabCap;
-            // the element into the bucket's records (a blind 2-B store; no read)
-            *GPTR(uint16_t, !(o1v && !full) ? reinterpret_cast<uintptr_t>(tab2) + kDummy6 : rec_addr(tab, tab2, p, t1)) =
-                static_cast<uint16_t>(a | (v << 8));
-            x0 = (sym && order == 0) ? v : x0;
-            const bool fl = sym && o.n >= o.cap;                           // compress.c:617
-            claims += (o1v && !fl) ? 1u : 0u;
-            const bool rs0 = sym && nodes >= kMaxNodes;                    // compress.c:148-157
-            const bool lv = past || full || (rs0 && !can_reset6(rst, o.n + 1));
-            off = off || lv;
-            fail = fail || fl;
-            done = done || eos || lv || fl;
-            sink1_put(o, v, sym && !lv && !fl);
-            a = sym ? p : a;
-            p = sym ? v : p;
-            order += (sym && order < 2) ? 1u : 0u;
-            repeat = sym ? false : repeat;
-            o2s = sym ? false : o2s;
-            e2d = go ? (e2 && need) : e2d;
-            stall = stall || need;
-            if (rare_lane(rs0 && !done)) {
-                if (rs0 && !done) reset6(root, stats, R, rtot, rrt, order, a, p, nodes, nh, repeat, o2s, e2d, seg0, rst, o.n);
-            }
-#ifdef DEC6_STATS_PREFETCH
-            stn = stats[p];                           // (the next step's bucket byte, read ahead)
-            {
-                const uint32_t nt = stn & 31u, nd1 = nt - (stn >> 5);
-                rtn = rcp64(max(kSubEscDelta * nd1 + kSubDelta * nt, 1u));
-            }
-#endif
-            PROF(0)
-            if constexpr (kSlot) slot_step_end(in, ssl, shc);
-            else src_adv(in);
-            PROF(5)
+            rtot = (rtot + kRootDelta) & 0xFFFF;
         }
+        if (rare_lane(sym && (1 + cnt0 > 0xFF - 2 * kRootDelta + 1 || rtot > kTotalLimit))) {
+            if (sym && (1 + cnt0 > 0xFF - 2 * kRootDelta + 1 || rtot > kTotalLimit))
+                rtot = root3_rescale<false>(root, R);
+        }
+        rrt = sym ? rcp64(rtot) : rrt;
+        // the element joins bucket p: new to its order-2 context (never visited) and,
+        // by the assumption above, to order 1; nodes as compress.c creates them
+        nodes += sym ? (cnt0 == 0 ? 1u : 0u) + (order >= 1 ? 1u : 0u) + (order >= 2 ? 1u : 0u) : 0u;
+        const bool o1v = sym && order >= 1;
+#ifndef DEC6_STATS_PREFETCH
+        stats[p] = static_cast<uint8_t>(o1v ? st + 1 : sraw);   // (written on every path: no exec mask)
+#else
+        if (o1v) stats[p] = static_cast<uint8_t>(st + 1);
+#endif
+        const bool full = o1v && t1 >= kTabCap;
+        // the element into the bucket's records (a blind 2-B store; no read)
+        *GPTR(uint16_t, !(o1v && !full) ? reinterpret_cast<uintptr_t>(tab2) + kDummy6 : rec_addr(tab, tab2, p, t1)) =
+            static_cast<uint16_t>(a | (v << 8));
+        x0 = (sym && order == 0) ? v : x0;
+        const bool fl = sym && o.n >= o.cap;                           // compress.c:617
+        claims += (o1v && !fl) ? 1u : 0u;
+        const bool rs0 = sym && nodes >= kMaxNodes;                    // compress.c:148-157
+        const bool lv = past || full || (rs0 && !can_reset6(rst, o.n + 1));
+        off = off || lv;
+        fail = fail || fl;
+        done = done || eos || lv || fl;
+        sink1_put(o, v, sym && !lv && !fl);
+        a = sym ? p : a;
+        p = sym ? v : p;
+        order += (sym && order < 2) ? 1u : 0u;
+        repeat = sym ? false : repeat;
+        o2s = sym ? false : o2s;
+        e2d = go ? (e2 && need) : e2d;
+        stall = stall || need;
+        if (rare_lane(rs0 && !done)) {
+            if (rs0 && !done) reset6(root, stats, R, rtot, rrt, order, a, p, nodes, nh, repeat, o2s, e2d, seg0, rst, o.n);
+        }
+#ifdef DEC6_STATS_PREFETCH
+        stn = stats[p];                           // (the next step's bucket byte, read ahead)
+        {
+            const uint32_t nt = stn & 31u, nd1 = nt - (stn >> 5);
+            rtn = rcp64(max(kSubEscDelta * nd1 + kSubDelta * nt, 1u));
+        }
+#endif
+        PROF(0)
+        if constexpr (kSlot) slot_step_end(in, ssl, shc);
+        else src_adv(in);
+        PROF(5)
+    };
+    // A block: kBlock6 common steps (fewer once no lane can take one), then the
+    // rare phase, whose lanes load their records and wait for them.
+    // -DDEC6_TAIL=K (1-3; measured, not the default: DESIGN.md §7): kBlock6 - K
+    // looped steps, the record loads of the lanes stalled so far (rc_dec6_rare.h
+    // rec_request), K more steps written out behind them, then the phase.
+    uint32_t s = 0;
+    for (;;) {
+#if DEC6_TAIL == 0
+        step();
         ++s;
         if (s < kBlock6 && any_lane(!done && !stall)) continue;
         s = 0;
+        Hist6 H;
+        const bool pre = false;
+#else
+        // (the looped steps as a loop of their own: with the tail and the phase
+        // in the same loop body the kernel needs 224 VGPRs and runs slower; this
+        // form in turn costs 1 % without a tail, DESIGN_HISTORY)
+        s = 0;
+        bool can;
+        do {
+            step();
+            ++s;
+            can = any_lane(!done && !stall);
+        } while (s < kBlock6 - kTail6 && can);
+        Hist6 H;
+        bool pre = false;                     // H holds the requested records (wave-uniform)
+        if (can) {
+            const bool pf = stall && !done;
+            const uint32_t pst = pf && order >= 1 ? stats[p] : 0u;
+            uint4 r1, r2, r3, r4;
+            rec_request(tab, tab2, dum ? dum : tab2 + kDummy6, p, pst & 31u, pf, r1, r2, r3);
+            step();
+#if DEC6_TAIL > 1
+            step();
+#endif
+#if DEC6_TAIL > 2
+            step();
+#endif
+            // the lanes that stalled in the tail load here: a full wait where there is one
+            // (leaving them to the next phase instead measured no better, DESIGN_HISTORY)
+            const bool sv = stall && !done;
+            const uint32_t sst = sv && order >= 1 ? stats[p] : 0u;
+            rec_late(tab, tab2, p, sst & 31u, sv && !pf, r1, r2, r3);
+            rec_take(tab2, p, sst & 31u, sv, r1, r2, r3, r4);
+            rec_fill(r1, r2, r3, r4, p, sst & 31u, hl, nh, x0, o.n - seg0, sv, H);
+            pre = true;
+        }
+#endif
         // ------------------------------------------------------------ rare phase
         for (uint32_t it = 0; it < kRareIters6 && any_lane(stall && !done); ++it) {
             const bool rs = stall && !done;
@@ -399,8 +452,9 @@ DEV void decompress_one6(const rc_batch_dev& bt, const rc_workspace_dev& ws, uin
 #endif
             const uint32_t st = rs && order >= 1 ? stats[p] : 0u;
             const uint32_t t1 = st & 31u, d1 = t1 - (st >> 5);
-            Hist6 H;
-            rec_build(tab, tab2, p, rs ? t1 : 0u, hl, nh, x0, o.n - seg0, rs, H);
+            // (a block that ended early requested nothing, and a lane's second
+            // rare step is on a new bucket: loaded here, and waited for)
+            if (!pre || it > 0) rec_build(tab, tab2, p, rs ? t1 : 0u, hl, nh, x0, o.n - seg0, rs, H);
             const bool over = false;
             PROF(1)
 #ifdef RC_PROFILE
@@ -439,27 +493,40 @@ DEV void decompress_one6(const rc_batch_dev& bt, const rc_workspace_dev& ws, uin
                 if (sub_decode6(pl, g1, t1, d1, c1, low, code, range, in, v, hu, hc, sf)) at = 1;
             }
             // the root, or the hit's interval
+            // (a stall is a hit at order 1 or 2 but for a double escape: the root's
+            // division, search and update only where some lane of the wavefront is there)
             const bool rg = rs && !over && !sf && at < 0;
-            const uint32_t r0 = udiv16d(range, rtot, rrt);
-            const uint32_t cd0 = udiv_lo16(code - low, r0);
-            const bool eos = rg && cd0 < 1;
-            const bool past = rg && !eos && cd0 - 1 >= rtot - 1;
-            const bool sym0 = rg && !eos && !past;
-            range = sym0 ? r0 : range;
+            bool eos = false, past = false, sym0 = false;
             uint32_t under0 = 0, cnt0 = 0;
-            const uint32_t v0 = root3_search(root, R, sym0 ? cd0 - 1 : 0u, under0, cnt0);
+#ifndef DEC6_ROOT_ALWAYS
+            if (any_lane(rg))
+#endif
+            {
+                const uint32_t r0 = udiv16d(range, rtot, rrt);
+                const uint32_t cd0 = udiv_lo16(code - low, r0);
+                eos = rg && cd0 < 1;
+                past = rg && !eos && cd0 - 1 >= rtot - 1;
+                sym0 = rg && !eos && !past;
+                range = sym0 ? r0 : range;
+                const uint32_t v0 = root3_search(root, R, sym0 ? cd0 - 1 : 0u, under0, cnt0);
+                v = sym0 ? v0 : v;
+            }
             const bool sym = sym0 || at > 0;
-            v = sym0 ? v0 : v;
             dec_code(low, code, range, sym0 ? 1 + under0 : hu, sym0 ? 1 + cnt0 : hc, in, sym);
-            if (sym0) {
-                root3_add_inc(root, R, itab, v, cnt0);
-                rtot = (rtot + kRootDelta) & 0xFFFF;
+#ifndef DEC6_ROOT_ALWAYS
+            if (any_lane(sym0))
+#endif
+            {
+                if (sym0) {
+                    root3_add_inc(root, R, itab, v, cnt0);
+                    rtot = (rtot + kRootDelta) & 0xFFFF;
+                }
+                if (rare_lane(sym0 && (1 + cnt0 > 0xFF - 2 * kRootDelta + 1 || rtot > kTotalLimit))) {
+                    if (sym0 && (1 + cnt0 > 0xFF - 2 * kRootDelta + 1 || rtot > kTotalLimit))
+                        rtot = root3_rescale<false>(root, R);
+                }
+                rrt = sym0 ? rcp64(rtot) : rrt;
             }
-            if (rare_lane(sym0 && (1 + cnt0 > 0xFF - 2 * kRootDelta + 1 || rtot > kTotalLimit))) {
-                if (sym0 && (1 + cnt0 > 0xFF - 2 * kRootDelta + 1 || rtot > kTotalLimit))
-                    rtot = root3_rescale<false>(root, R);
-            }
-            rrt = sym0 ? rcp64(rtot) : rrt;
             PROF(2)
             // the element joins its contexts (compress.c:598-615)
             const uint32_t eqv = peq6(pl, v) & km;
@@ -615,6 +682,8 @@ extern "C" __global__ __launch_bounds__(512) void rc_decompress_dec6s(rc_batch_d
     uint8_t* tab = static_cast<uint8_t*>(ws.dec6_pool) + static_cast<size_t>(slot) * kTab1;
     uint8_t* tab2 = static_cast<uint8_t*>(ws.dec6_pool) + static_cast<size_t>(ws.lane_slots) * kTab1 +
                     static_cast<size_t>(slot) * kTab2;
+    // the line every lane without a record to request loads instead (slot 0's dummy slots)
+    const uint8_t* dum = static_cast<uint8_t*>(ws.dec6_pool) + static_cast<size_t>(ws.lane_slots) * kTab1 + kDummy6;
     const uint32_t* order = ws.order && !ws.bins[RC_LEN_BINS] ? ws.order : nullptr;
     // the decoding wavefront ahead of its helper when both can issue (-0.5 %,
     // profiles/r4e_dec6_prio.txt; -DDEC6_PRIO=0: equal)
@@ -623,7 +692,7 @@ extern "C" __global__ __launch_bounds__(512) void rc_decompress_dec6s(rc_batch_d
     in.gen = 0; in.mctl = mctl; in.hctl = hctl; in.slot = slotp;
     for (uint32_t i = slot; i < b.n; i += gridDim.x * kLanes6s) {
         const uint32_t pkt = order ? order[i] : i;
-        decompress_one6(b, ws, pkt, root, stats, tab, tab2, itab, in, rtab);
+        decompress_one6(b, ws, pkt, root, stats, tab, tab2, itab, in, rtab, dum);
     }
     mctl[1] = kFinS;
 }

@@ -89,8 +89,83 @@ DEV void rec_load(const uint8_t* tab, const uint8_t* tab2, uint32_t p, uint32_t 
     }
 }
 
+// ---- records requested ahead of the rare phase (rc_dec6.hip, DEC6_TAIL) ----
+// rec_request issues the loads some steps before the phase and nothing waits
+// for them there; rec_take, behind those steps, is their first use, so the
+// compiler's wait in front of it counts the stores issued since (one element
+// store per step) and leaves them in flight: vmcnt(n), n >= DEC6_TAIL.
+//
+// The loads are unconditional, as the step's own memory operations are: a
+// lane with nothing to request reads the line at dum, which all such lanes
+// share.  What makes an early load of a stalled lane's records safe:
+//   * a stalled lane stores only to its dummy slot, so its records do not
+//     change between the load and its rare step;
+//   * its own earlier stores to them precede the load in program order, as
+//     they precede the load inside the phase;
+//   * reset6 runs only for a lane that decoded a symbol, never a stalled one;
+//   * a wave bail ends every lane of the wavefront: what was loaded is dropped.
+
+// a load result made to arrive inside the (rare) branch that issued it: read
+// behind the join, it would put that branch's wait -- for everything in
+// flight -- on the common path too
+DEV void rec_settle(uint4& r)
+{
+#ifndef RC_LANE_HOST_TEST
+    asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
+#endif
+}
+
+DEV uint4 sel16(bool c, const uint4& x, const uint4& y)
+{
+    return make_uint4(c ? x.x : y.x, c ? x.y : y.y, c ? x.z : y.z, c ? x.w : y.w);
+}
+
+// bucket p's 16-B record where en, and the first 32 B of its 48-B record where t1 > 8
+DEV void rec_request(const uint8_t* tab, const uint8_t* tab2, const uint8_t* dum, uint32_t p, uint32_t t1, bool en,
+                     uint4& r1, uint4& r2, uint4& r3)
+{
+    const uintptr_t d = reinterpret_cast<uintptr_t>(dum);
+    const uintptr_t b2 = reinterpret_cast<uintptr_t>(tab2) + kTab2Rec * p;
+    const bool big = en && t1 > 8;
+    r1 = hload16(en ? reinterpret_cast<uintptr_t>(tab) + 16 * p : d);
+    r2 = hload16(big ? b2 : d);
+    r3 = hload16(big ? b2 + 16 : d + 16);
+}
+
+// the same for lanes nothing was requested for (en), loaded and waited for here
+DEV void rec_late(const uint8_t* tab, const uint8_t* tab2, uint32_t p, uint32_t t1, bool en, uint4& r1, uint4& r2,
+                  uint4& r3)
+{
+    if (any_lane(en)) {
+        const uintptr_t b2 = reinterpret_cast<uintptr_t>(tab2) + kTab2Rec * p;
+        uint4 l1 = r1, l2 = r2, l3 = r3;
+        if (en) l1 = hload16(reinterpret_cast<uintptr_t>(tab) + 16 * p);
+        if (en && t1 > 8) {
+            l2 = hload16(b2);
+            l3 = hload16(b2 + 16);
+        }
+        rec_settle(l1); rec_settle(l2); rec_settle(l3);
+        r1 = l1; r2 = l2; r3 = l3;
+    }
+}
+
+// the requested records as rec_load returns them: zero where not loaded; the
+// 48-B record's last 16 B (t1 > 24) loaded here
+DEV void rec_take(const uint8_t* tab2, uint32_t p, uint32_t t1, bool en, uint4& r1, uint4& r2, uint4& r3, uint4& r4)
+{
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    r1 = sel16(en, r1, z);
+    r2 = sel16(en && t1 > 8, r2, z);
+    r3 = sel16(en && t1 > 8, r3, z);
+    r4 = z;
+    if (rare_lane(en && t1 > 24)) {
+        if (en && t1 > 24) r4 = hload16(reinterpret_cast<uintptr_t>(tab2) + kTab2Rec * p + 32);
+        rec_settle(r4);
+    }
+}
+
 DEV void rec_fill(const uint4& r1, const uint4& r2, const uint4& r3, const uint4& r4, uint32_t p, uint32_t t1,
-                  const uint32_t* hl, uint32_t nh, uint32_t x0, uint32_t n, Hist6& H)
+                  const uint32_t* hl, uint32_t nh, uint32_t x0, uint32_t n, bool en, Hist6& H)
 {
     H.A[0] = bperm(r1.y, r1.x, 0x06040200u); H.V[0] = bperm(r1.y, r1.x, 0x07050301u);
     H.A[1] = bperm(r1.w, r1.z, 0x06040200u); H.V[1] = bperm(r1.w, r1.z, 0x07050301u);
@@ -103,10 +178,20 @@ DEV void rec_fill(const uint4& r1, const uint4& r2, const uint4& r3, const uint4
     H.p1 = (p == x0 && t1 > 0 && n >= 2) ? 1u : 0u;
     H.hit = 0u;
     uint32_t k = t1;
+    // (an order-2 hit of the bucket a lane stalls in: rare, and a wavefront has
+    // some lane with a hit somewhere for most of its packets' length -- each
+    // hit's merge only where a served lane (en) has one in its bucket)
+#ifdef DEC6_HITS_ALWAYS
     if (any_lane(nh > 0))
+#endif
 #pragma unroll
     for (uint32_t h = 0; h < 4; ++h) {
+#ifdef DEC6_HITS_ALWAYS
         const bool mine = h < nh && (hl[h] & 0xFFu) == p;
+#else
+        const bool mine = en && h < nh && (hl[h] & 0xFFu) == p;
+        if (!any_lane(mine)) continue;
+#endif
         const uint32_t ks = 8 * (k & 3);
 #pragma unroll
         for (uint32_t d = 0; d < 8; ++d) {
@@ -131,7 +216,7 @@ DEV void rec_build(const uint8_t* tab, const uint8_t* tab2, uint32_t p, uint32_t
 {
     uint4 r1, r2, r3, r4;
     rec_load(tab, tab2, p, t1, en, r1, r2, r3, r4);
-    rec_fill(r1, r2, r3, r4, p, t1, hl, nh, x0, n, H);
+    rec_fill(r1, r2, r3, r4, p, t1, hl, nh, x0, n, en, H);
 }
 
 // The values of a bucket's elements as bit planes: bit j of pl[b] is bit b of
