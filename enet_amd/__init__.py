@@ -161,6 +161,24 @@ class RangeCoder:
             raise RuntimeError(f"enet_rc_crc32_batch_device failed: HIP error {rc}")
         return crc_out
 
+    def pack_batch(self, out, out_off, out_len, packed, stream=None):
+        """enet_rc_pack_batch_device: out_len[i] bytes of every packet (at
+        out_off[i] of out) back to back into packed, which holds at least the
+        sum of out_len.  Device tensors; returns packed."""
+        import torch
+        for t in (out, out_off, out_len, packed):
+            if not (t.is_cuda and t.is_contiguous()):
+                raise ValueError("batch tensors must be contiguous device tensors")
+        assert out.dtype == torch.uint8 and packed.dtype == torch.uint8
+        assert out_off.dtype == torch.int64 and out_len.dtype == torch.int32
+        if stream is None:
+            stream = torch.cuda.current_stream(out.device)
+        rc = self.lib.enet_rc_pack_batch_device(self.ctx, out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(),
+                                                out_len.numel(), packed.data_ptr(), C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"enet_rc_pack_batch_device failed: HIP error {rc}")
+        return packed
+
     def crc32(self, data: bytes) -> int:
         """One datagram through the host-pointer batch path (like enet_crc32 on one buffer)."""
         src = C.create_string_buffer(bytes(data) + b"\0")

@@ -140,7 +140,11 @@ int enet_rc_compress_gather_batch_host(void *context, const ENetBuffer *buffers,
  * in[in_off[i] .. +in_len[i]): CRC-32/IEEE, returned in network byte order
  * exactly like the reference (ENET_HOST_TO_NET_32 of the complement), i.e.
  * the value protocol.c:1709-1718 writes into the datagram header and
- * protocol.c:1075-1091 compares.  Device / host pointer variants as above. */
+ * protocol.c:1075-1091 compares.  Device / host pointer variants as above.
+ * The device variant loads the whole aligned 16-byte granules around each
+ * packet's range (as does the gather of a host batch from mapped memory), so
+ * every granule that holds a byte of a packet must be readable device memory;
+ * bytes outside the range do not affect the result. */
 int enet_rc_crc32_batch_device(void *context, const uint8_t *in, const uint64_t *in_off,
                                const uint32_t *in_len, size_t n, uint32_t *crc_out, void *stream);
 int enet_rc_crc32_batch_host(void *context, const uint8_t *in, const uint64_t *in_off,
